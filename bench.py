@@ -7,8 +7,12 @@ Workload (BASELINE.json configs[2], the configuration the metric is quoted on):
 One "step" = one pass of the hot path over the whole batch:
     random-policy kernel -> mrx_cim_step (action + ticks until the next decision) -> snapshot query.
 value = decision events resolved per second, whole job (all ranks), state resident in HBM.
+A plain run sets up, warms up, times exactly --steps steps and prints the line; --full adds everything else (end-to-end and
+sustained legs, oracle parity, CPU baselines, roofline, the secondary configurations).  --dump-outputs DIR writes what the
+last timed step computed as DIR/<name>.npy (with --collect: the experiences of the last timed call).
 
     python bench.py --gpus 1 --steps 400 --warmup 100
+    python bench.py --gpus 1 --steps 400 --warmup 100 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 """
@@ -73,6 +77,33 @@ def frame_bytes(topo):
             return v
     P, V = topo.n_ports, topo.n_vessels
     return P * 48 + V * (9 * 4 + 2 + (2 * topo.past_stop_number + 2 * topo.future_stop_number) * 4) + 4 * (P * P + 2 * V * P)
+
+
+DUMP_MAX_BYTES = 64 << 20   # --dump-outputs: the files of one run, in all
+
+
+def group_outputs(parts):
+    """{name: [device tensor of each group, or None]} -> {name: host numpy array}, the groups' env rows joined in env order."""
+    import torch
+    return {k: torch.cat(ts).cpu().numpy() for k, ts in parts.items() if ts and all(t is not None for t in ts)}
+
+
+def write_outputs(folder, arrays, seed=0):
+    """--dump-outputs: every array of `arrays` ({name: numpy array}) as <folder>/<name>.npy — float32 / float64 as they are, integers
+    and flags as float64 (exact: every value here is far below 2**53).  Should they exceed DUMP_MAX_BYTES in all, each array keeps
+    the same fixed, seeded sample of its rows in every run, and <name>.rows.npy lists which."""
+    import numpy as np
+    os.makedirs(folder, exist_ok=True)
+    conv = {k: (a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)) for k, a in ((k, np.asarray(a)) for k, a in arrays.items())}
+    budget = DUMP_MAX_BYTES * 0.9   # (room for the .npy headers)
+    sample = sum(a.nbytes for a in conv.values()) > budget
+    frac = budget / sum(a.nbytes + (8 * a.shape[0] if a.ndim else 0) for a in conv.values())   # (8 bytes: a row's entry in its list)
+    for name, a in conv.items():
+        if sample and a.ndim and a.shape[0] > 1:
+            rows = np.sort(np.random.default_rng(seed).choice(a.shape[0], max(1, int(a.shape[0] * frac)), replace=False))
+            a = a[rows]
+            np.save(os.path.join(folder, f"{name}.rows.npy"), rows.astype(np.float64))
+        np.save(os.path.join(folder, f"{name}.npy"), np.ascontiguousarray(a))
 
 
 def host_cores():
@@ -336,21 +367,28 @@ def bench_citi_bike(args, dist, dev, rank, world):
         sync_all()
         dt = time.perf_counter() - t0
         windows.append((dt, sum(float(b["counter"].item()) for b in bufs), total("ticks") - tick0, t_issued))
+    if args.dump_outputs and rank == 0:   # what the last timed step handed its caller (engine.step's tensors, the policy's actions, the slice)
+        write_outputs(args.dump_outputs, group_outputs({
+            "decisions": [e.decisions for e in engines], "scope": [e.scope for e in engines], "metrics": [e.metrics for e in engines],
+            "done": [e.done for e in engines], "actions": [b["actions"] for b in bufs], "n_actions": [b["n_actions"] for b in bufs],
+            "obs_stations": [b.get("obs") for b in bufs], "query_stations": [b["q_out"] for b in bufs]}))
     n_done = int(total("done"))
     status_bad = sum(int((e.status != 0).sum().item()) for e in engines)
-    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(min(args.steps, 100))]
-    for a, b in ev:       # (group 0's step launch alone on its stream: informational)
-        eng.random_policy(step_i, bufs[0]["actions"], bufs[0]["n_actions"], None)
-        a.record(streams[0])
-        eng.step(bufs[0]["actions"], bufs[0]["n_actions"])
-        b.record(streams[0])
-        step_i += 1
-    torch.cuda.synchronize(dev)
-    step_kernel_ms = sum(a.elapsed_time(b) for a, b in ev) / len(ev)
+    step_kernel_ms = None
+    if args.full:
+        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(min(args.steps, 100))]
+        for a, b in ev:       # (group 0's step launch alone on its stream: informational)
+            eng.random_policy(step_i, bufs[0]["actions"], bufs[0]["n_actions"], None)
+            a.record(streams[0])
+            eng.step(bufs[0]["actions"], bufs[0]["n_actions"])
+            b.record(streams[0])
+            step_i += 1
+        torch.cuda.synchronize(dev)
+        step_kernel_ms = sum(a.elapsed_time(b) for a, b in ev) / len(ev)
     # the same loop with bounded steps (mrx_cb_set_step_budget): a call no longer waits for the batch's longest env-step; envs
     # without a decision yet are skipped by the policy and continue in the next call.  Reported beside `value`, not as it.
     bounded = None
-    if args.bounded_budget and not args.step_budget:
+    if args.full and args.bounded_budget and not args.step_budget:
         for e in engines:
             e.set_step_budget(args.bounded_budget)
         for _ in range(args.warmup):
@@ -373,7 +411,7 @@ def bench_citi_bike(args, dist, dev, rank, world):
     # the one exchange step of a sharded rollout: 32 steps of (decision, action, metrics, done) per env gathered to the
     # learner rank over RCCL (maro_amd/cim/rollout.py::gather_to_learner); outside the timed env-step window
     gather_ms = None
-    if dist is not None:
+    if dist is not None and args.full:
         from maro_amd.cim.rollout import gather_to_learner
         T = 32
         traj = {"decisions": torch.zeros((T, n, 8), dtype=torch.int32, device=dev), "actions": torch.zeros((T, n, 1, 3), dtype=torch.int32, device=dev),
@@ -396,7 +434,7 @@ def bench_citi_bike(args, dist, dev, rank, world):
             assert out["decisions"].shape[1] == n * world
     # parity (untimed, every rank's own engine; rank 0 reports): sampled envs of THIS engine replayed on the pure-Python oracle
     parity = None
-    if args.parity_envs > 0 and rank == 0:
+    if args.full and args.parity_envs > 0 and rank == 0:
         from tests.bench_parity import replay_citi_bike_against_oracle
         torch.cuda.synchronize(dev)
         eng.use_stream(None)      # (group 0's engine, on torch's current stream for the replay)
@@ -423,8 +461,6 @@ def bench_citi_bike(args, dist, dev, rank, world):
     ms_per_step = dt / args.steps * 1e3
     from maro_amd import _lib as mrx_lib
     code_key = f"{getattr(eng, 'code_object_key', None)}+{mrx_lib.source_hash('cb')}"   # step kernels' code object + the library's sources (policy / query kernels)
-    traffic, basis = measured_bytes_citi_bike(topology, n, args.step_budget, code_key, G, args.replay_period)
-    achieved = None if traffic is None else traffic / (ms_per_step * 1e-3) / 1e9     # per GPU: bytes of one batch step / its wall time
     out = {
         "metric": f"env-steps/sec (decision events/sec), citi_bike {topology}",
         "value": resolved / dt, "unit": "env-steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -436,19 +472,22 @@ def bench_citi_bike(args, dist, dev, rank, world):
                    "env_major_state": bool(eng.layout.env_major), "ring_slots": 16, "parallelism": f"env-shard x{world} (no data-path collective); {G} independent group(s) per GPU on separate HIP streams",
                    "trajectory_gather_ms_32_steps": gather_ms, "mean_ticks_per_env_step": tbar, "envs_finished_in_window": n_done, "env_status_errors": status_bad,
                    "step_budget": args.step_budget, "replay_period": args.replay_period},
-        "roofline": {"bound": "hbm", "kernel": "mrx_k_cb_step" if not eng.layout.env_major else "mrx_k_cb_step_wave + mrx_k_cb_replay_wave (+ query, policy)",
-                     "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": None if achieved is None else achieved / HBM_PEAK_GBPS,
-                     "traffic": traffic, "basis": basis, "kernel_ms": step_kernel_ms, "env_steps_per_launch": n,
-                     "note": "latency-bound by construction (SURVEY.md 8d: ~1 KB per env-step): the batch step lasts as long as its longest env-step's dependent chain; "
-                             "frac is measured bytes / wall time of a batch step and is null when no PMC record of this exact build exists"},
     }
+    if args.full:
+        traffic, basis = measured_bytes_citi_bike(topology, n, args.step_budget, code_key, G, args.replay_period)
+        achieved = None if traffic is None else traffic / (ms_per_step * 1e-3) / 1e9     # per GPU: bytes of one batch step / its wall time
+        out["roofline"] = {"bound": "hbm", "kernel": "mrx_k_cb_step" if not eng.layout.env_major else "mrx_k_cb_step_wave + mrx_k_cb_replay_wave (+ query, policy)",
+                           "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": None if achieved is None else achieved / HBM_PEAK_GBPS,
+                           "traffic": traffic, "basis": basis, "kernel_ms": step_kernel_ms, "env_steps_per_launch": n,
+                           "note": "latency-bound by construction (SURVEY.md 8d: ~1 KB per env-step): the batch step lasts as long as its longest env-step's dependent chain; "
+                                   "frac is measured bytes / wall time of a batch step and is null when no PMC record of this exact build exists"}
     if bounded:
         out["bounded_steps"] = {"budget_records": args.bounded_budget, "value": resolved_b / dtb, "unit": "env-steps/s", "ms_per_call": dtb / args.steps * 1e3,
                                 "decisions_per_call_per_env": resolved_b / (args.steps * n * world),
                                 "what": "same loop with mrx_cb_set_step_budget: a call stops after ~budget events per env; envs without a decision yet continue in the next call (trajectories unchanged)"}
     if parity is not None:
         out["parity"] = parity
-    if world == 1 and not args.no_cpu:
+    if args.full and world == 1 and not args.no_cpu:
         ref = cpu_baseline_citi_bike_reference(topology, min(durations, 1440), res, args.cpu_seconds)
         port = cpu_baseline_citi_bike(topology, min(durations, 1440), res, args.cpu_seconds if ref is None or "error" in ref else min(args.cpu_seconds, 5.0))
         if ref is not None and "error" not in ref:
@@ -752,10 +791,14 @@ def bench_collect(args, engines, streams, qnet, chains, n, G, dev, rank, world, 
             dist.barrier()
             torch.cuda.synchronize(dev)
 
+    last = [None]
+
     def one_call(k):
         # the groups' step generators advanced in turn: every engine is bound to its group's stream (use_stream), the sampler puts
         # its own tensor ops on that stream too, and a step is a few C-ABI calls — the groups' kernels overlap like in the headline loop
         res = sample_fused_groups(samplers, qnet, k, seeds=seeds_of, reset_every=args.reset_every)
+        if args.dump_outputs:
+            last[0] = res
         return sum(int(r["tick"].shape[0]) for r in res)
 
     # untimed: into mid-episode (the first reward window must have passed for experiences to flow), then the warmup
@@ -780,22 +823,29 @@ def bench_collect(args, engines, streams, qnet, chains, n, G, dev, rank, world, 
             dist.all_reduce(t, op=dist.ReduceOp.SUM)
             t[0] = tm[0]
         dts.append(float(t[0])); vals.append(float(t[1]) / float(t[0])); exps.append(float(t[2]) / float(t[0]))
-    # the policy launches alone (act of every group, back to back, no record / step): its own MFMA roofline
-    b_act = [dict(a=torch.zeros((e.n_envs, 1, 4), dtype=torch.int32, device=dev), n=torch.zeros(e.n_envs, dtype=torch.int32, device=dev)) for e in engines]
-    sync_all()
-    reps = 20
-    t0 = time.perf_counter()
-    for _ in range(reps):
-        for g in range(G):
-            qnet[g].act(b_act[g]["a"], b_act[g]["n"])
-    torch.cuda.synchronize(dev)
-    act_ms = (time.perf_counter() - t0) / reps * 1e3
-    deciding = sum(int((e.decisions[:, 7] == 1).sum().item()) for e in engines)
+    if args.dump_outputs and rank == 0:   # the experiences the last timed call returned, every group's joined (env ids of the whole rank)
+        goff = [sum(e.n_envs for e in engines[:g]) for g in range(G)]
+        res = [dict(r, env_id=r["env_id"] + goff[g]) for g, r in enumerate(last[0])]
+        write_outputs(args.dump_outputs, group_outputs({k: [r[k] for r in res] for k, v in res[0].items() if isinstance(v, torch.Tensor)}))
+    last[0] = None
+    act_ms = deciding = None
+    if args.full:
+        # the policy launches alone (act of every group, back to back, no record / step): its own MFMA roofline
+        b_act = [dict(a=torch.zeros((e.n_envs, 1, 4), dtype=torch.int32, device=dev), n=torch.zeros(e.n_envs, dtype=torch.int32, device=dev)) for e in engines]
+        sync_all()
+        reps = 20
+        t0 = time.perf_counter()
+        for _ in range(reps):
+            for g in range(G):
+                qnet[g].act(b_act[g]["a"], b_act[g]["n"])
+        torch.cuda.synchronize(dev)
+        act_ms = (time.perf_counter() - t0) / reps * 1e3
+        deciding = sum(int((e.decisions[:, 7] == 1).sum().item()) for e in engines)
     # ---- N > 1: the learner-side collection (outside the timed windows): one more call, its experiences joined on rank 0
     # (gather_experiences_to_learner: ragged sizes, one grouped send / receive), and the return path: the learner's packed
     # networks broadcast to every rank's actors (broadcast_policy)
     exp_gather = policy_bcast = None
-    if dist is not None:
+    if dist is not None and args.full:
         from maro_amd.cim.rollout import broadcast_policy, gather_experiences_to_learner
         sync_all()
         ta = time.perf_counter()
@@ -826,7 +876,7 @@ def bench_collect(args, engines, streams, qnet, chains, n, G, dev, rank, world, 
                         "networks + an in-place set_policy_state on every group's actor"}
     # ---- parity (untimed; rank 0's own envs): the loop's own elements of a few envs replayed on the C oracle
     parity = None
-    if args.parity_envs > 0 and rank == 0:
+    if args.full and args.parity_envs > 0 and rank == 0:
         from tests.bench_parity import replay_collect_against_oracle
         parity = replay_collect_against_oracle(samplers, qnet, seeds_of, None, args.topology, k=min(args.parity_envs, 6), num_steps=384,
                                                reset_every=args.reset_every, chains=chains)
@@ -836,9 +886,6 @@ def bench_collect(args, engines, streams, qnet, chains, n, G, dev, rank, world, 
     ms_per_step = dts[med] / args.steps * 1e3
     from maro_amd import _lib as mrx_lib
     code_key = f"{getattr(engines[0], 'code_object_key', None)}+{mrx_lib.source_hash('cim')}"   # step kernels' code object + the library's sources (DQN / sampler kernels)
-    traffic, basis = measured_bytes_collect(n, G, code_key)
-    achieved = None if traffic is None else traffic / (ms_per_step * 1e-3) / 1e9
-    tf = DQN_FLOPS_PER_ENV * deciding / (act_ms * 1e-3) / 1e12
     out = {"metric": "env-steps/sec while collecting experiences (CimBatchSampler.sample_fused), CIM global_trade.22p",
            "value": vals[med], "unit": "env-steps/s", "experiences_per_s": exps[med], "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
            "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "int32+f64 (env), f32 MFMA (policy)",
@@ -848,17 +895,21 @@ def bench_collect(args, engines, streams, qnet, chains, n, G, dev, rank, world, 
                       "envs_per_gpu": n, "groups_per_gpu": G, "reset_every": args.reset_every, "specialized_kernels": bool(engines[0].specialized), "code_object_key": code_key,
                       "reset_ms_whole_batch": reset_ms, "look_back": samplers[0].look_back, "reward_window": samplers[0].time_window,
                       "experience_gather": exp_gather, "policy_broadcast": policy_bcast,
-                      "what_a_step_is": "one sample_fused interaction of every env: mrx_cim_dqn_act + the transition-cache update + mrx_cim_step; per call: mrx_cim_sampler_emit"},
-           "roofline": {"bound": "hbm", "kernel": "the whole loop (mrx_k_cim_dqn_prep, mrx_k_cim_dqn_mlp16, mrx_k_cim_step_tab, mrx_k_cim_sampler_emit_all, ...)", "achieved": achieved, "peak": HBM_PEAK_GBPS,
-                        "unit": "GB/s", "frac": None if achieved is None else achieved / HBM_PEAK_GBPS, "traffic": traffic, "basis": basis,
-                        "note": "bytes of one batch interaction (all kernels) / its wall time; null when no PMC record of this exact build exists"},
-           "roofline_policy": {"bound": "mfma", "kernel": "mrx_k_cim_dqn_mlp16 (+ mrx_k_cim_dqn_prep: binning + state rows)", "achieved": tf, "peak": MFMA_F32_PEAK_TFLOPS, "unit": "TFLOP/s",
-                               "frac": tf / MFMA_F32_PEAK_TFLOPS, "dtype": "f32 (v_mfma_f32_16x16x4_f32)", "kernel_ms": act_ms, "deciding_envs": deciding,
-                               "flops_per_env": DQN_FLOPS_PER_ENV, "basis": "algorithmic flops (2 x sum(in x out) of the example's layers x deciding envs) / wall time of the act "
-                               "launches of all groups issued back to back with nothing else on the GPU"}}
+                      "what_a_step_is": "one sample_fused interaction of every env: mrx_cim_dqn_act + the transition-cache update + mrx_cim_step; per call: mrx_cim_sampler_emit"}}
+    if args.full:
+        traffic, basis = measured_bytes_collect(n, G, code_key)
+        achieved = None if traffic is None else traffic / (ms_per_step * 1e-3) / 1e9
+        tf = DQN_FLOPS_PER_ENV * deciding / (act_ms * 1e-3) / 1e12
+        out["roofline"] = {"bound": "hbm", "kernel": "the whole loop (mrx_k_cim_dqn_prep, mrx_k_cim_dqn_mlp16, mrx_k_cim_step_tab, mrx_k_cim_sampler_emit_all, ...)", "achieved": achieved, "peak": HBM_PEAK_GBPS,
+                           "unit": "GB/s", "frac": None if achieved is None else achieved / HBM_PEAK_GBPS, "traffic": traffic, "basis": basis,
+                           "note": "bytes of one batch interaction (all kernels) / its wall time; null when no PMC record of this exact build exists"}
+        out["roofline_policy"] = {"bound": "mfma", "kernel": "mrx_k_cim_dqn_mlp16 (+ mrx_k_cim_dqn_prep: binning + state rows)", "achieved": tf, "peak": MFMA_F32_PEAK_TFLOPS, "unit": "TFLOP/s",
+                                  "frac": tf / MFMA_F32_PEAK_TFLOPS, "dtype": "f32 (v_mfma_f32_16x16x4_f32)", "kernel_ms": act_ms, "deciding_envs": deciding,
+                                  "flops_per_env": DQN_FLOPS_PER_ENV, "basis": "algorithmic flops (2 x sum(in x out) of the example's layers x deciding envs) / wall time of the act "
+                                  "launches of all groups issued back to back with nothing else on the GPU"}
     if parity is not None:
         out["parity"] = parity
-    if world == 1 and not args.no_cpu:
+    if args.full and world == 1 and not args.no_cpu:
         ref = cpu_baseline_collect(args.topology, engines[0].durations if engines[0].durations <= 1120 else 1120, min(args.cpu_seconds, 12.0))
         if ref is not None:
             out["cpu_baseline"] = ref
@@ -1025,8 +1076,14 @@ def main():
                     "resets overlapped with the other groups' steps (0: skip)")
     ap.add_argument("--episode-block", type=int, default=32, help="(kept for old command lines; the end-to-end leg polls every group every 32 batch steps without a device-wide sync)")
     ap.add_argument("--parity-envs", type=int, default=64, help="envs replayed on the CPU oracle after the run (0: off)")
-    ap.add_argument("--repeats", type=int, default=5, help="the timed window (exactly --steps steps between barrier + synchronize) is run this many "
-                    "times back to back; `value` is the median window, value_min / value_max the spread")
+    ap.add_argument("--repeats", type=int, default=None, help="the timed window (exactly --steps steps between barrier + synchronize) is run this many "
+                    "times back to back; `value` is the median window, value_min / value_max the spread (default 1; 5 with --full)")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline figure: end-to-end and sustained legs, oracle parity, CPU "
+                    "baselines, per-kernel timing and roofline, trajectory gathers, bounded steps, the secondary configurations.  Without it a run "
+                    "sets up, warms up, times --steps steps, writes --dump-outputs and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the timed path computed in its last "
+                    "step (the arrays its caller receives; rank 0's envs) as DIR/<name>.npy in float32 / float64, at most 64 MB in all.  With "
+                    "--collect: the experiences the last timed sample_fused_groups call returned, i.e. all --steps interactions of that call")
     ap.add_argument("--gather-every", type=int, default=0, help="N > 1 ranks: additionally roll out K-step trajectories and gather each to the learner "
                     "(gather_to_learner), reporting the gather's share of a rollout (0: only the single 32-step gather)")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
@@ -1034,14 +1091,21 @@ def main():
     ap.add_argument("--object-api", action="store_true", help="run ONLY the object-API leg (GpuVectorEnv.step(list of Action), env_view stepping) and print it")
     ap.add_argument("--secondary", type=int, default=-1, help="after the headline (cim, random agent), also run BASELINE configs 4 and 5 as short legs and embed "
                     "them under `secondary` in the same JSON line (citi_bike toy.3s_4t 4096 envs — and, on one GPU, all 32768 of config 4; DQN collection loop 8192 envs), each with parity, "
-                    "cpu_baseline and a measured-bytes roofline.  -1 = auto: on for the default workload (what the driver runs), off when a flag selects another one")
+                    "cpu_baseline and a measured-bytes roofline.  -1 = auto: on for the default workload with --full, off without it or when a flag selects another workload")
     args = ap.parse_args()
     explicit_envs = args.envs is not None
     if args.envs is None:
         args.envs = 16384 if args.scenario == "cim" else 4096
+    # the CIM episode is sized for the windows of a --full run (5 unless --repeats says otherwise), so that a plain run and a
+    # --full run with the same --steps simulate the same episode length
+    args.episode_windows = 5 if args.repeats is None else args.repeats
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
     if args.secondary < 0:
-        args.secondary = int(args.scenario == "cim" and args.policy == "random" and not args.collect and not explicit_envs and not args.graphs
+        args.secondary = int(args.full and args.scenario == "cim" and args.policy == "random" and not args.collect and not explicit_envs and not args.graphs
                              and args.topology == "global_trade.22p_l0.8" and args.obs == "fused" and not args.no_query)
+    if args.dump_outputs and args.object_api:
+        raise SystemExit("--dump-outputs: the object-API leg has no timed-step outputs to write")
 
     import torch
 
@@ -1068,6 +1132,7 @@ def main():
             a4 = copy.copy(args)
             a4.scenario, a4.envs, a4.topology, a4.durations, a4.step_budget, a4.bounded_budget = "citi_bike", 4096, "toy.3s_4t", 1120, 0, 0
             a4.parity_envs = min(args.parity_envs, 8)
+            a4.dump_outputs = None   # (--dump-outputs holds the headline's outputs only)
             r4 = bench_citi_bike(a4, dist, dev, rank, world)
             gc.collect()
             torch.cuda.empty_cache()
@@ -1097,6 +1162,7 @@ def main():
             a5.policy, a5.collect, a5.envs, a5.ring, a5.no_episode = "dqn", True, 8192, max(args.ring, 8), True
             a5.groups = 2    # (a latency-bound three-launch chain per group: measured 1 / 2 / 3 groups = 59 / 65 / 62 M at this size)
             a5.parity_envs = min(args.parity_envs, 6)
+            a5.dump_outputs = None
             r5 = bench_cim(a5, dist, dev, rank, world)
             r_obj = None
             if world == 1:
@@ -1136,8 +1202,9 @@ def bench_cim(args, dist, dev, rank, world):
     # The per-GPU batch is split into G independent groups, each with its own engine and HIP stream: the kernels of the
     # other groups fill a group's launch gaps and tail.  Envs never interact, so this is pure scheduling.
     n, G = args.envs, max(1, args.groups)
-    # the episode must outlast the run (finished envs would idle): ~0.45 ticks per env-step on 22p
-    need_ticks = args.preroll_ticks + int(0.55 * (args.warmup + args.steps * max(1, args.repeats) + min(args.steps, 100) + 64)) + 64
+    # the episode must outlast the run (finished envs would idle): ~0.45 ticks per env-step on 22p; sized for the --full
+    # run's windows (args.episode_windows), which also covers the single window of a plain run
+    need_ticks = args.preroll_ticks + int(0.55 * (args.warmup + args.steps * max(1, args.episode_windows) + min(args.steps, 100) + 64)) + 64
     sim_durations = max(args.durations, need_ticks)
     obs_mode = "none" if args.no_query else args.obs
     # --agent fused: the random legal agent answered inside the step kernel (one launch per batch step and group); no policy launch
@@ -1286,32 +1353,41 @@ def bench_cim(args, dist, dev, rank, world):
         gpu_busy_s["timed_windows"] += dt
         # decisions answered inside the window (K policy calls per group in the window)
         windows.append({"dt": dt, "resolved": sum(int(b["counter"].item()) for b in bufs), "ticks": total_ticks() - tick0, "t_issued": t_issued})
+    if args.dump_outputs and rank == 0:   # what the last timed step handed its caller (engine.step's tensors, the agent's actions, the slices)
+        obs = [b.get("obs") or (None, None) for b in bufs]
+        write_outputs(args.dump_outputs, group_outputs({
+            "decisions": [e.decisions for e in engines], "metrics": [e.metrics for e in engines], "done": [e.done for e in engines],
+            "actions": [b["actions"] for b in bufs], "n_actions": [b["n_actions"] for b in bufs],
+            "obs_ports": [o[0] for o in obs], "obs_vessel": [o[1] for o in obs],
+            "query_ports": [b["q_ports"] for b in bufs], "query_vessel": [b["q_vessel"] for b in bufs]}))
     n_done = sum(int(e.done.sum().item()) for e in engines)
     status_bad = sum(int((e.status != 0).sum().item()) for e in engines)
 
     # ---- dominant kernel (the step kernel) timed live with HIP events, each pair on the stream of its launch, in the same
     # interleaved schedule as the timed loop (informational: roofline.achieved comes from the timed window above)
-    reps = min(args.steps, 100)
-    ev = [[tuple(torch.cuda.Event(enable_timing=True) for _ in range(3)) for _ in range(G)] for _ in range(reps)]
-    sync_all()
-    t_ev = time.perf_counter()
-    for r in range(reps):
-        for g in range(G):
-            one_step(step_i, g, timing=ev[r][g])
-        step_i += 1
-    torch.cuda.synchronize(dev)
-    gpu_busy_s["event_timed_steps"] = time.perf_counter() - t_ev
-    durs = [a.elapsed_time(b) for row in ev for a, b, _ in row]
-    policy_ms = sum(c.elapsed_time(a) for row in ev for a, _, c in row) / len(durs) if qnet is not None else None
-    step_kernel_ms = sum(durs) / len(durs)                      # mean duration of one launch (ng envs; sorted launch: + the schedule kernel)
-    span_ms = max([ev[0][g][0].elapsed_time(ev[-1][g2][1]) for g in range(G) for g2 in range(G)]) if G > 1 else sum(durs)
-    in_flight = max(1.0, sum(durs) / span_ms) if G > 1 else 1.0    # mean number of step kernels running concurrently
+    policy_ms = step_kernel_ms = in_flight = None
+    if args.full:
+        reps = min(args.steps, 100)
+        ev = [[tuple(torch.cuda.Event(enable_timing=True) for _ in range(3)) for _ in range(G)] for _ in range(reps)]
+        sync_all()
+        t_ev = time.perf_counter()
+        for r in range(reps):
+            for g in range(G):
+                one_step(step_i, g, timing=ev[r][g])
+            step_i += 1
+        torch.cuda.synchronize(dev)
+        gpu_busy_s["event_timed_steps"] = time.perf_counter() - t_ev
+        durs = [a.elapsed_time(b) for row in ev for a, b, _ in row]
+        policy_ms = sum(c.elapsed_time(a) for row in ev for a, _, c in row) / len(durs) if qnet is not None else None
+        step_kernel_ms = sum(durs) / len(durs)                      # mean duration of one launch (ng envs; sorted launch: + the schedule kernel)
+        span_ms = max([ev[0][g][0].elapsed_time(ev[-1][g2][1]) for g in range(G) for g2 in range(G)]) if G > 1 else sum(durs)
+        in_flight = max(1.0, sum(durs) / span_ms) if G > 1 else 1.0    # mean number of step kernels running concurrently
 
     # ---- the one exchange step of a sharded rollout (north_star: RCCL "only to gather trajectories to the learner"): 32 steps of
     # (decision, action, metrics, done, fused observation) per env from every rank to rank 0 in ONE collective
     # (maro_amd/cim/rollout.py::gather_to_learner); outside the timed env-step window
     gather_ms = gather_bytes = gather_every = None
-    if dist is not None:
+    if dist is not None and args.full:
         from maro_amd.cim.rollout import gather_to_learner
 
         def alloc_traj(T):
@@ -1374,7 +1450,7 @@ def bench_cim(args, dist, dev, rank, world):
     # ---- end to end (untimed window of its own): reset of the whole batch + one complete episode of every env, the same
     # agent; envs that finish early keep being stepped (they report done) until the slowest one is through
     episode = None
-    if not args.no_episode and qnet is None and not args.graphs:
+    if args.full and not args.no_episode and qnet is None and not args.graphs:
         if sim_durations != args.durations:   # (only very long runs stretch the episode: measure the nominal one on fresh engines)
             del engines[:]
             torch.cuda.empty_cache()
@@ -1486,7 +1562,7 @@ def bench_cim(args, dist, dev, rank, world):
     # ---- parity (untimed): a sample of envs of THIS configuration replayed on the CPU oracle — every decision, metric,
     # fused observation and the final snapshot ring (tests/bench_parity.py; the oracle is the checker, never the thing measured)
     parity = None
-    if args.parity_envs > 0 and qnet is None and not args.graphs and world == 1:
+    if args.full and args.parity_envs > 0 and qnet is None and not args.graphs and world == 1:
         from tests.bench_parity import replay_against_oracle
         parity = replay_against_oracle(engines, bufs, streams, sizes, offs, rank * n, args.topology, engines[0].durations, args.parity_envs,
                                        obs=bufs[0].get("obs") is not None)
@@ -1517,60 +1593,8 @@ def bench_cim(args, dist, dev, rank, world):
         value = resolved / dt
         ms_per_step = dt / args.steps * 1e3
         tbar = ticks_adv / max(resolved, 1.0)  # mean ticks advanced per env-step
-        F = frame_bytes(topo)
-        b_step = (3.0 + tbar) * F + 4.0 * topo.n_targets * tbar + 40.0  # fixed per-env-step formula
         ng = n / G                                  # env-steps per launch
-        kernel = ("mrx_k_cim_step_tab" if engines[0].layout.order_table_on else "mrx_k_cim_step") + ("_obs" if bufs[0].get("obs") is not None else "")
-        # HBM bytes one launch really moves: the committed PMC passes of this same workload AND this same code object
-        # (tools/gpu_profile.sh -> tools/refresh_pmc.py -> profiles/latest_pmc.json, stamped with the step kernels' cache key =
-        # hash of plan text + device sources + flags + toolchain); any other build falls back to the algorithmic bytes
-        traffic = pmc_src = None
-        pmc_state = "no profiles/latest_pmc.json"
         code_key = getattr(engines[0], "code_object_key", None)
-        try:
-            with open(os.path.join(REPO, "profiles", "latest_pmc.json")) as fp:
-                pmc = json.load(fp)
-            if not (pmc["topology"] == args.topology and abs(pmc["envs_per_launch"] - ng) <= 1 and pmc.get("kernel") == kernel):
-                pmc_state = "the record is of another configuration"
-            elif pmc.get("code_object_key") != code_key or code_key is None:
-                pmc_state = f"the record is of another build (code object {pmc.get('code_object_key')}, running {code_key})"
-            else:
-                traffic = (2.0 * pmc["fetch_size_kib"] + pmc["write_size_kib"]) * 1024.0
-                pmc_src = {k: pmc.get(k) for k in ("source", "git_head", "code_object_key", "code_object_sha16", "bench_value", "date")}
-                pmc_state = "matched"
-        except Exception:
-            pass
-        # the measured ceiling of this access pattern (tools/hbm_pattern_bench: same grid, LDS reservation, pieces and streams, no
-        # simulation work), committed by the same profile run
-        ceiling = None
-        try:
-            with open(os.path.join(REPO, "profiles", "pattern_ceiling.json")) as fp:
-                pc = json.load(fp)
-            if pc.get("topology") == args.topology and abs(pc["envs_per_launch"] - ng) <= 1:
-                ceiling = pc
-        except Exception:
-            pass
-        alg_per_launch = b_step * (resolved / world / args.steps / G)   # SURVEY formula bytes of one launch (its env-steps x B_step)
-        alg_gbps = alg_per_launch * G / (ms_per_step * 1e-3) / 1e9
-        if traffic is not None:
-            # achieved = bytes the kernel really moves per launch x launches per step / the TIMED window's ms_per_step (per GPU)
-            achieved = traffic * G / (ms_per_step * 1e-3) / 1e9
-            basis = "measured HBM bytes (PMC: 2 x FETCH_SIZE + WRITE_SIZE per launch) x launches per step / ms_per_step of the timed window"
-        else:
-            # the record of the SAME code object at another batch size: its bytes per env-step carry over (the per-env access list
-            # does not depend on the batch); any other build has no measured bytes -> no fraction (never the SURVEY formula)
-            achieved = basis = None
-            try:
-                if pmc.get("code_object_key") == code_key and code_key is not None and pmc.get("kernel") == kernel and pmc["topology"] == args.topology:
-                    traffic = (2.0 * pmc["fetch_size_kib"] + pmc["write_size_kib"]) * 1024.0 / pmc["envs_per_launch"] * ng
-                    achieved = traffic * G / (ms_per_step * 1e-3) / 1e9
-                    pmc_src = {k: pmc.get(k) for k in ("source", "git_head", "code_object_key", "code_object_sha16", "bench_value", "date")}
-                    basis = (f"measured HBM bytes per env-step of the same code object (PMC record at {pmc['envs_per_launch']:.0f} envs per launch) scaled to "
-                             f"{ng:.0f} envs per launch x launches per step / ms_per_step of the timed window")
-            except Exception:
-                pass
-            if achieved is None:
-                basis = f"no measured bytes for this build ({pmc_state}): frac is null — run tools/gpu_profile.sh to refresh profiles/latest_pmc.json"
         out = {
             "metric": "env-steps/sec (decision events/sec), CIM global_trade.22p",
             "value": value, "unit": "env-steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -1589,22 +1613,75 @@ def bench_cim(args, dist, dev, rank, world):
                        "trajectory_gather_ms_32_steps": gather_ms, "trajectory_gather_bytes_per_rank": gather_bytes, "trajectory_gather_every": gather_every,
                        "untimed_preroll_steps": preroll_steps, "mean_tick_at_window_start": tick_mean0,
                        "mean_ticks_per_env_step": tbar, "envs_finished_in_window": n_done, "env_status_errors": status_bad},
-            "roofline": {"bound": "hbm", "kernel": kernel, "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                         "frac": None if achieved is None else achieved / HBM_PEAK_GBPS, "traffic": traffic, "traffic_source": pmc_src, "basis": basis,
-                         "bytes_per_env_step": None if traffic is None else traffic / ng,
-                         "kernel_ms": step_kernel_ms, "launches_in_flight": in_flight, "env_steps_per_launch": ng, "launches_per_step": G,
-                         "survey_formula": {"bytes_per_env_step": b_step, "bytes_per_launch": alg_per_launch, "GBps_if_the_engine_moved_them": alg_gbps,
-                                            "measured_over_formula_bytes": None if traffic is None else traffic / alg_per_launch,
-                                            "note": "SURVEY.md 8(d)'s fixed formula (reference dtypes, every snapshot copy counted).  The engine moves a fraction of these "
-                                                    "bytes (aliased pre-decision snapshot, compact frame, HBM-direct fast path), so this is a statement about eliminated "
-                                                    "copies, NOT a bandwidth figure, and it never feeds `frac`"}},
         }
-        if ceiling is not None:
-            # value / (env-steps/s the no-compute pattern reaches) — both whole-batch rates on one GPU
-            out["roofline"]["pattern_ceiling"] = {"env_steps_per_s": ceiling["env_steps_per_s"], "GBps": ceiling["GBps"], "frac_of_peak": ceiling["GBps"] / HBM_PEAK_GBPS,
-                                                  "value_over_ceiling": (value / world) / ceiling["env_steps_per_s"], "source": ceiling.get("source"),
-                                                  "what": "tools/hbm_pattern_bench: the step kernel's loads / stores per env-step (same grid, LDS reservation, piece sizes, "
-                                                          "sorted launch, 3 streams) with no simulation work"}
+        if args.full:
+            F = frame_bytes(topo)
+            b_step = (3.0 + tbar) * F + 4.0 * topo.n_targets * tbar + 40.0  # fixed per-env-step formula
+            kernel = ("mrx_k_cim_step_tab" if engines[0].layout.order_table_on else "mrx_k_cim_step") + ("_obs" if bufs[0].get("obs") is not None else "")
+            # HBM bytes one launch really moves: the committed PMC passes of this same workload AND this same code object
+            # (tools/gpu_profile.sh -> tools/refresh_pmc.py -> profiles/latest_pmc.json, stamped with the step kernels' cache key =
+            # hash of plan text + device sources + flags + toolchain); any other build falls back to the algorithmic bytes
+            traffic = pmc_src = None
+            pmc_state = "no profiles/latest_pmc.json"
+            try:
+                with open(os.path.join(REPO, "profiles", "latest_pmc.json")) as fp:
+                    pmc = json.load(fp)
+                if not (pmc["topology"] == args.topology and abs(pmc["envs_per_launch"] - ng) <= 1 and pmc.get("kernel") == kernel):
+                    pmc_state = "the record is of another configuration"
+                elif pmc.get("code_object_key") != code_key or code_key is None:
+                    pmc_state = f"the record is of another build (code object {pmc.get('code_object_key')}, running {code_key})"
+                else:
+                    traffic = (2.0 * pmc["fetch_size_kib"] + pmc["write_size_kib"]) * 1024.0
+                    pmc_src = {k: pmc.get(k) for k in ("source", "git_head", "code_object_key", "code_object_sha16", "bench_value", "date")}
+                    pmc_state = "matched"
+            except Exception:
+                pass
+            # the measured ceiling of this access pattern (tools/hbm_pattern_bench: same grid, LDS reservation, pieces and streams, no
+            # simulation work), committed by the same profile run
+            ceiling = None
+            try:
+                with open(os.path.join(REPO, "profiles", "pattern_ceiling.json")) as fp:
+                    pc = json.load(fp)
+                if pc.get("topology") == args.topology and abs(pc["envs_per_launch"] - ng) <= 1:
+                    ceiling = pc
+            except Exception:
+                pass
+            alg_per_launch = b_step * (resolved / world / args.steps / G)   # SURVEY formula bytes of one launch (its env-steps x B_step)
+            alg_gbps = alg_per_launch * G / (ms_per_step * 1e-3) / 1e9
+            if traffic is not None:
+                # achieved = bytes the kernel really moves per launch x launches per step / the TIMED window's ms_per_step (per GPU)
+                achieved = traffic * G / (ms_per_step * 1e-3) / 1e9
+                basis = "measured HBM bytes (PMC: 2 x FETCH_SIZE + WRITE_SIZE per launch) x launches per step / ms_per_step of the timed window"
+            else:
+                # the record of the SAME code object at another batch size: its bytes per env-step carry over (the per-env access list
+                # does not depend on the batch); any other build has no measured bytes -> no fraction (never the SURVEY formula)
+                achieved = basis = None
+                try:
+                    if pmc.get("code_object_key") == code_key and code_key is not None and pmc.get("kernel") == kernel and pmc["topology"] == args.topology:
+                        traffic = (2.0 * pmc["fetch_size_kib"] + pmc["write_size_kib"]) * 1024.0 / pmc["envs_per_launch"] * ng
+                        achieved = traffic * G / (ms_per_step * 1e-3) / 1e9
+                        pmc_src = {k: pmc.get(k) for k in ("source", "git_head", "code_object_key", "code_object_sha16", "bench_value", "date")}
+                        basis = (f"measured HBM bytes per env-step of the same code object (PMC record at {pmc['envs_per_launch']:.0f} envs per launch) scaled to "
+                                 f"{ng:.0f} envs per launch x launches per step / ms_per_step of the timed window")
+                except Exception:
+                    pass
+                if achieved is None:
+                    basis = f"no measured bytes for this build ({pmc_state}): frac is null — run tools/gpu_profile.sh to refresh profiles/latest_pmc.json"
+            out["roofline"] = {"bound": "hbm", "kernel": kernel, "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                               "frac": None if achieved is None else achieved / HBM_PEAK_GBPS, "traffic": traffic, "traffic_source": pmc_src, "basis": basis,
+                               "bytes_per_env_step": None if traffic is None else traffic / ng,
+                               "kernel_ms": step_kernel_ms, "launches_in_flight": in_flight, "env_steps_per_launch": ng, "launches_per_step": G,
+                               "survey_formula": {"bytes_per_env_step": b_step, "bytes_per_launch": alg_per_launch, "GBps_if_the_engine_moved_them": alg_gbps,
+                                                  "measured_over_formula_bytes": None if traffic is None else traffic / alg_per_launch,
+                                                  "note": "SURVEY.md 8(d)'s fixed formula (reference dtypes, every snapshot copy counted).  The engine moves a fraction of these "
+                                                          "bytes (aliased pre-decision snapshot, compact frame, HBM-direct fast path), so this is a statement about eliminated "
+                                                          "copies, NOT a bandwidth figure, and it never feeds `frac`"}}
+            if ceiling is not None:
+                # value / (env-steps/s the no-compute pattern reaches) — both whole-batch rates on one GPU
+                out["roofline"]["pattern_ceiling"] = {"env_steps_per_s": ceiling["env_steps_per_s"], "GBps": ceiling["GBps"], "frac_of_peak": ceiling["GBps"] / HBM_PEAK_GBPS,
+                                                      "value_over_ceiling": (value / world) / ceiling["env_steps_per_s"], "source": ceiling.get("source"),
+                                                      "what": "tools/hbm_pattern_bench: the step kernel's loads / stores per env-step (same grid, LDS reservation, piece sizes, "
+                                                              "sorted launch, 3 streams) with no simulation work"}
         if episode is not None:
             ep_s = float(ep_t.item())
             out["value_end_to_end"] = ep_steps_all / ep_s
@@ -1622,7 +1699,7 @@ def bench_cim(args, dist, dev, rank, world):
             out["config"]["value_end_to_end"] = out["value_end_to_end"]
         if parity is not None:
             out["parity"] = parity
-        if world == 1 and not args.no_cpu:
+        if args.full and world == 1 and not args.no_cpu:
             out["cpu_baseline"] = cpu_baseline(args.topology, args.durations, args.cpu_seconds)
             # the reference's own Env.step / VectorEnv, timed live on this box's host cores from the shipped build (oracle/_ref)
             ref = cpu_baseline_reference(args.topology, args.durations, args.cpu_seconds)
@@ -1639,7 +1716,7 @@ def bench_cim(args, dist, dev, rank, world):
                     ref = None
             if ref is not None:
                 out["cpu_baseline_reference"] = ref
-        if qnet is not None:
+        if args.full and qnet is not None:
             # the policy's own roofline: exact-f32 MFMA (MI355X_MICROARCH.md: 157.3 TFLOP/s), algorithmic flops = 2 x sum(in x out)
             # of the example's real layer sizes x the deciding envs of one launch; mrx_cim_dqn_act = bin + forward kernels
             fl = 2.0 * sum(a * b for a, b in ((171, 256), (256, 128), (128, 64), (64, 32), (32, 128), (32, 128), (128, 21), (128, 1)))

@@ -1,7 +1,8 @@
 """Native readers of MARO's on-disk data (maro_amd/data_lib.py, CimTopology load_data_folder, citi_bike load_build_folder):
 the product needs no MARO checkout to compile a CIM dump / real-data folder or a citi_bike build folder.  Round trips on
-folders written here in the reference's formats; and, where the reference checkout / its built toy data happen to be
-present (the build container), byte-for-byte agreement with the topologies the reference's own loaders produced."""
+folders written here in the reference's formats; the reference's own CIM real-data fixture folders (kept under
+tests/golden/cim_case_data/) against the topologies its loaders produced; and the citi_bike toys' build folders, read
+with the reference's own toy config.yml files (tests/golden/cb_toy_topologies/), against the packaged topologies."""
 import json
 import os
 
@@ -10,10 +11,9 @@ import pytest
 
 from maro_amd.data_lib import items_in_range, pick_ticks, read_binary, write_binary
 
-REF_CIM = "/root/reference/tests/data/cim/case_data"
-REF_CB_BUILD = "/tmp/oracle/home/.maro/data/citi_bike/.build"
-REF_CB_TOPO = "/root/reference/maro/simulator/scenarios/citi_bike/topologies"
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+CIM_CASE_DATA = os.path.join(GOLDEN, "cim_case_data")   # the reference's tests/data/cim/case_data real-data folders
+CB_TOY_TOPOLOGIES = os.path.join(GOLDEN, "cb_toy_topologies")   # the reference's citi_bike topologies/<toy>/config.yml
 
 
 def test_binary_round_trip(tmp_path):
@@ -77,12 +77,11 @@ def test_cim_real_data_folder_csv_and_binary_compile_to_the_same_topology(tmp_pa
     assert a.fixed_vessel_period.tolist() == [3 * 1 + 2 + 3 + 3, 2 * 2 + 2 + 2]
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_CIM), reason="reference fixtures not present (build container only)")
 @pytest.mark.parametrize("folder,gold", [("real_folder_csv", "real_folder_csv"), ("real_folder_bin", "real_folder_bin")])
 def test_cim_reference_fixture_folders_compile_to_the_committed_topologies(folder, gold):
     """tests/golden/topology_<gold>.json was written in round 1 from the reference's OWN loaders (cim_data_loader.py:360-450)."""
     from maro_amd.cim.topology import CimTopology, load_data_folder
-    t = load_data_folder(os.path.join(REF_CIM, folder), name=gold)
+    t = load_data_folder(os.path.join(CIM_CASE_DATA, folder), name=gold)
     g = CimTopology.from_json(open(os.path.join(GOLDEN, f"topology_{gold}.json")).read())
     assert json.loads(t.to_json()) == json.loads(g.to_json())
 
@@ -129,13 +128,19 @@ def test_citi_bike_build_folder_loader(tmp_path):
     assert (ts.min() + 60 * first_midnight - t0) // 86400 == 1 and (ts.min() + 60 * (first_midnight - 1) - t0) // 86400 == 0
 
 
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REF_CB_BUILD, "toy.3s_4t")) or not os.path.isdir(REF_CB_TOPO), reason="built toy data not present (build container only)")
 @pytest.mark.parametrize("name", ["toy.3s_4t", "toy.4s_4t", "toy.5s_6t"])
-def test_citi_bike_packaged_topologies_are_what_the_native_loader_compiles(name):
+def test_citi_bike_packaged_topologies_are_what_the_native_loader_compiles(name, tmp_path):
     """The packaged maro_amd/citi_bike/topologies/<name>.npz were compiled in round 1 with the reference's BinaryReader /
-    ItemTickPicker / WeatherTable; the native loader must produce the same arrays from the same build folder."""
+    ItemTickPicker / WeatherTable.  Their build folder, as the golden tooling writes it for the reference's Env
+    (oracle/setup_toy_topologies.py: trips.bin, KNYC_daily.bin, station_meta.csv, distance_adj.csv), read by the native loader
+    with the reference's own config.yml of the toy, must give back the same arrays and decision settings."""
     from maro_amd.citi_bike.data import load_build_folder, load_topology
-    d, g = load_build_folder(os.path.join(REF_CB_TOPO, name, "config.yml"), os.path.join(REF_CB_BUILD, name), name=name, is_holiday=None), load_topology(name)
+    from maro_amd.citi_bike.synthetic import write_build_folder
+    from oracle.setup_toy_topologies import start_utc_of, weather_rows
+    g = load_topology(name)
+    t0 = start_utc_of(g)
+    write_build_folder(g, str(tmp_path / name), t0, weather=weather_rows(g, t0))
+    d = load_build_folder(os.path.join(CB_TOY_TOPOLOGIES, name, "config.yml"), str(tmp_path / name), name=name, is_holiday=None)
     for k in ("trip_tick", "trip_src", "trip_dst", "trip_duration", "capacity", "init_bikes", "station_id", "distance", "tick_day", "day_weekday",
               "day_holiday", "day_weather", "day_temperature"):
         assert np.array_equal(getattr(d, k), getattr(g, k)), k

@@ -1,5 +1,5 @@
-"""bench.py's output contract (one JSON line on stdout with the driver's keys plus `roofline` and `cpu_baseline`), checked on a
-tiny batch so it costs seconds."""
+"""bench.py's output contract (one JSON line on stdout with the driver's keys; with --full also `roofline` and `cpu_baseline`),
+checked on a tiny batch so it costs seconds."""
 import json
 import os
 import subprocess
@@ -11,8 +11,8 @@ pytestmark = pytest.mark.gpu
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def run_bench(*extra):
-    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "3", *extra],
+def run_bench(*extra, full=True):
+    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "3", *(("--full",) if full else ()), *extra],
                          capture_output=True, text=True, cwd=REPO, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -51,9 +51,9 @@ def test_bench_line_contract(extra):
 
 
 def test_bench_default_line_carries_configs_4_and_5():
-    """The driver's exact command: after the headline, BASELINE configs 4 (citi_bike toy.3s_4t, 4096 envs) and 5 (the DQN collection
+    """The driver's command with --full: after the headline, BASELINE configs 4 (citi_bike toy.3s_4t, 4096 envs) and 5 (the DQN collection
     loop, 8192 envs) run as short legs and ride in the same JSON line, each with parity, cpu_baseline and an honest roofline."""
-    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--cpu-seconds", "4"],
+    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--full", "--cpu-seconds", "4"],
                          capture_output=True, text=True, cwd=REPO, timeout=1500)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -99,7 +99,7 @@ def test_bench_multi_rank_path_under_gloo(scenario, world):
     port = s.getsockname()[1]
     s.close()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(REPO, "bench.py"), "--gpus", str(world), "--steps", "8", "--warmup", "3",
+           "--master-port", str(port), os.path.join(REPO, "bench.py"), "--gpus", str(world), "--steps", "8", "--warmup", "3", "--full",
            "--scenario", scenario, "--envs", "256" if scenario == "cim" else "128", "--no-cpu"]
     if scenario == "cim":
         cmd += ["--preroll-ticks", "20", "--durations", "260", "--repeats", "2", "--gather-every", "16", "--no-episode", "--parity-envs", "0"]
@@ -124,7 +124,7 @@ def test_bench_multi_rank_path_under_gloo(scenario, world):
 
 
 def test_bench_default_command_on_two_ranks_under_gloo():
-    """The driver's N > 1 command as it is issued (`bench.py --gpus N --steps K --warmup W`, nothing else): the headline AND both
+    """The driver's N > 1 command with --full (`bench.py --gpus N --steps K --warmup W --full`): the headline AND both
     secondary legs run on every rank (barriers, max-over-ranks times, summed counts, the trajectory / experience gathers and the
     policy broadcast of config 5), and rank 0 prints one line whose secondary values are whole-job aggregates."""
     env = dict(os.environ, MRX_BENCH_BACKEND="gloo", MRX_BENCH_DEVICE="0", MASTER_ADDR="127.0.0.1")
@@ -134,7 +134,7 @@ def test_bench_default_command_on_two_ranks_under_gloo():
     port = s.getsockname()[1]
     s.close()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "12", "--warmup", "4"]
+           "--master-port", str(port), os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "12", "--warmup", "4", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, cwd=REPO, timeout=1500, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.strip().startswith("{")]
@@ -159,7 +159,7 @@ def test_bench_collect_multi_rank_path_under_gloo():
     s.close()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(REPO, "bench.py"), "--gpus", "2", "--policy", "dqn", "--collect", "--ring", "8", "--steps", "24",
-           "--warmup", "4", "--repeats", "1", "--envs", "192", "--durations", "260", "--preroll-ticks", "40", "--no-cpu"]
+           "--warmup", "4", "--full", "--repeats", "1", "--envs", "192", "--durations", "260", "--preroll-ticks", "40", "--no-cpu"]
     out = subprocess.run(cmd, capture_output=True, text=True, cwd=REPO, timeout=900, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.strip().startswith("{")]
@@ -170,3 +170,64 @@ def test_bench_collect_multi_rank_path_under_gloo():
     assert g["experiences"] > 0 and g["gather_ms"] > 0 and 0 < g["gather_share"] < 1
     # state + next_state + next_agent_state float32 [171] + action int64 + env_action int32 [4] + reward f32 + terminal + env_id / tick / agent int32
     assert g["bytes_all_ranks"] == g["experiences"] * (3 * 171 * 4 + 8 + 16 + 4 + 1 + 12)
+
+
+@pytest.mark.parametrize("extra", [("--envs", "192"), ("--scenario", "citi_bike", "--envs", "128")])
+def test_bench_plain_line_and_dumped_outputs(extra, tmp_path):
+    """A plain run (no --full) is the headline alone: one timed window of exactly --steps steps and none of the --full legs.
+    --dump-outputs writes the last timed step's arrays in float32 / float64 (64 MB at most), identical in two runs with the same arguments."""
+    import numpy as np
+    dumps = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        j = run_bench(*extra, "--dump-outputs", str(d), full=False)
+        for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config"):
+            assert key in j, key
+        assert j["steps"] == 6 and j["warmup"] == 3 and j["repeats"] == 1 and j["value"] > 0 and j["ms_per_step"] > 0
+        assert not any(key in j for key in ("roofline", "parity", "cpu_baseline", "end_to_end", "sustained", "secondary", "bounded_steps")), sorted(j)
+        files = sorted(os.listdir(d))
+        assert {"decisions.npy", "metrics.npy", "done.npy", "actions.npy"} <= set(files), files
+        arrays = {f: np.load(d / f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert sum(os.path.getsize(d / f) for f in files) <= 64 << 20
+        assert arrays["decisions.npy"].shape[0] == int(extra[-1]) and np.isfinite(arrays["metrics.npy"]).all()
+        check_dumped_values(arrays, j, "citi_bike" in extra)
+        dumps.append(arrays)
+    assert dumps[0].keys() == dumps[1].keys()
+    for f in dumps[0]:
+        assert np.array_equal(dumps[0][f], dumps[1][f]), f
+
+
+def check_dumped_values(arrays, line, citi_bike):
+    """What the engine guarantees of the state after a step, checked on the dumped arrays: they are the engine's live outputs of
+    the last timed step (mid-episode, every env pausing at a fresh decision), not a stale or zeroed buffer of the right shape."""
+    import numpy as np
+    dec, met, done = arrays["decisions.npy"].astype(np.int64), arrays["metrics.npy"], arrays["done.npy"]
+    act, na = arrays["actions.npy"].astype(np.int64), arrays["n_actions.npy"]
+    n = dec.shape[0]
+    e = np.arange(n)
+    assert not done.any() and (met >= 0).all() and (met[:, 0] > 0).all()
+    assert set(np.unique(na)) <= {0.0, 1.0} and na.any()
+    if citi_bike:
+        from maro_amd.citi_bike.data import load_topology
+        topo = load_topology("toy.3s_4t")
+        S = topo.n_stations
+        # decisions = (tick, station, type, frame, n_scope, valid, ...); scope = (station, max) pairs, the deciding station last
+        assert (dec[:, 5] == 1).all() and (dec[:, 0] > 0).all() and ((dec[:, 1] >= 0) & (dec[:, 1] < S)).all() and np.isin(dec[:, 2], (0, 1)).all()
+        ns = dec[:, 4]
+        assert (ns >= 1).all() and np.array_equal(arrays["scope.npy"][e, ns - 1, 0].astype(np.int64), dec[:, 1])
+        # stations x (bikes, shortage, trip_requirement, fulfillment, capacity, extra_cost, min_bikes) of the decision's frame
+        obs = arrays["obs_stations.npy"]
+        assert obs.shape == (n, S, 7) and np.array_equal(obs[:, :, 4], np.broadcast_to(topo.capacity, (n, S))) and (obs[:, :, 0] >= 0).all()
+        sel = act[na == 1, 0]
+        assert ((sel[:, :2] >= 0) & (sel[:, :2] < S)).all() and (sel[:, 2] >= 0).all()
+    else:
+        # decisions = (tick, port, vessel, scope.load, scope.discharge, early_discharge, frame, valid)
+        assert (dec[:, 7] == 1).all() and dec[:, 0].mean() >= line["config"]["mean_tick_at_window_start"] > 0
+        # the fused slices of the decision's frame: ports x (empty, full, ...) and the deciding vessel's (empty, full, remaining_space);
+        # the action scope the engine raised is computed from the same state
+        ports, vessel = arrays["obs_ports.npy"], arrays["obs_vessel.npy"]
+        assert np.array_equal(dec[:, 3], np.minimum(ports[e, dec[:, 1], 0], vessel[:, 2])) and (dec[:, 3] > 0).any()
+        assert np.array_equal(dec[:, 4], vessel[:, 0])
+        sel = act[na == 1, 0]   # (vessel, port, quantity, 0 = load | 1 = discharge) of the decisions the last step answered
+        assert ((sel[:, 1] >= 0) & (sel[:, 1] < ports.shape[1])).all() and (sel[:, 0] >= 0).all() and (sel[:, 2] >= 0).all() and np.isin(sel[:, 3], (0, 1)).all()

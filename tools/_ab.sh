@@ -3,7 +3,7 @@ O=gpurun_out/$1; shift
 mkdir -p $O
 for spec in "$@"; do
   tag=${spec%%|*}; rest=${spec#*|}; flags=${rest%%|*}; bflags=${rest#*|}
-  MARO_AMD_SPEC_FLAGS="$flags" python bench.py --steps 200 --warmup 20 --no-cpu --secondary 0 --parity-envs 16 --no-episode $bflags > $O/$tag.json 2> $O/$tag.err
+  MARO_AMD_SPEC_FLAGS="$flags" python bench.py --full --steps 200 --warmup 20 --no-cpu --secondary 0 --parity-envs 16 --no-episode $bflags > $O/$tag.json 2> $O/$tag.err
   python - <<P
 import json
 try:

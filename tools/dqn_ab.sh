@@ -16,7 +16,7 @@ except Exception as e:
     print(sys.argv[1], "FAILED", e)
 P
 }
-CF="--policy dqn --collect --ring 8 --envs 8192 --no-cpu --steps 64 --warmup 16"
+CF="--full --policy dqn --collect --ring 8 --envs 8192 --no-cpu --steps 64 --warmup 16"
 timeout 600 python bench.py $CF --groups 2 --parity-envs ${PARITY:-0} > $O/collect_g2.json 2> $O/collect_g2.err; line $O/collect_g2.json
 timeout 600 python bench.py $CF --groups 1 --parity-envs 0 > $O/collect_g1.json 2> $O/collect_g1.err; line $O/collect_g1.json
 for e in $EXTRA; do timeout 600 python bench.py $CF --groups $e --parity-envs 0 > $O/collect_g$e.json 2> $O/collect_g$e.err; line $O/collect_g$e.json; done

@@ -15,7 +15,7 @@ tag=$1; shift
 O=gpurun_out/$tag
 mkdir -p $O
 if [ "${HEADLINE:-1}" = "1" ]; then   # (HEADLINE=0: only the optional blocks below, e.g. CB=1 after a change to the citi_bike kernels alone)
-timeout 900 python bench.py "$@" > $O/bench_line.json 2> $O/bench_line.err; echo "bench rc $?"
+timeout 900 python bench.py --full "$@" > $O/bench_line.json 2> $O/bench_line.err; echo "bench rc $?"
 [ -x tools/hbm_pattern_bench ] || hipcc -O3 --offload-arch=gfx950 -o tools/hbm_pattern_bench tools/hbm_pattern_bench.hip   # (built from source: the binary is not tracked)
 timeout 120 tools/hbm_pattern_bench --json-out $O/pattern_ceiling.json > $O/pattern_line.json 2> $O/pattern.err; echo "pattern rc $?"
 B="python bench.py --steps 60 --warmup 50 --repeats 1 --no-cpu --no-episode --parity-envs 0 --secondary 0 $*"
@@ -48,7 +48,7 @@ if [ "${COLLECT:-0}" = "1" ]; then
   for envs in ${COLLECT_ENVS:-8192}; do
     C=$O/collect_$envs; mkdir -p $C
     CF="--policy dqn --collect --ring 8 --envs $envs --groups 2 --no-cpu --parity-envs 0"
-    timeout 300 python bench.py $CF --steps 64 --warmup 16 > $C/bench_line.json 2> $C/bench_line.err; echo "collect $envs bench rc $?"
+    timeout 300 python bench.py --full $CF --steps 64 --warmup 16 > $C/bench_line.json 2> $C/bench_line.err; echo "collect $envs bench rc $?"
     timeout 300 rocprofv3 --kernel-trace --stats -d $C/trace -o r -- python bench.py $CF --steps 64 --warmup 16 --repeats 2 > $C/trace_line.json 2> $C/trace.err; echo "collect $envs trace rc $?"
     timeout 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $C/fetch -o r -- python bench.py $CF --steps 64 --warmup 16 --repeats 1 > $C/fetch_line.json 2> $C/fetch.err; echo "collect $envs fetch rc $?"
     timeout 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $C/write -o r -- python bench.py $CF --steps 64 --warmup 16 --repeats 1 > $C/write_line.json 2> $C/write.err; echo "collect $envs write rc $?"
@@ -59,7 +59,7 @@ fi
 if [ "${BIG:-0}" = "1" ]; then
   Bg=$O/big65536; mkdir -p $Bg
   BB="python bench.py --envs 65536 --steps 60 --warmup 50 --repeats 1 --no-cpu --no-episode --parity-envs 0"
-  timeout 300 python bench.py --envs 65536 --steps 200 --warmup 50 --repeats 3 --no-cpu --no-episode --parity-envs 0 > $Bg/bench_line.json 2> $Bg/bench_line.err; echo "big bench rc $?"
+  timeout 300 python bench.py --full --envs 65536 --steps 200 --warmup 50 --repeats 3 --no-cpu --no-episode --parity-envs 0 > $Bg/bench_line.json 2> $Bg/bench_line.err; echo "big bench rc $?"
   timeout 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $Bg/fetch -o r -- $BB > $Bg/fetch_line.json 2> $Bg/fetch.err; echo "big fetch rc $?"
   timeout 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $Bg/write -o r -- $BB > $Bg/write_line.json 2> $Bg/write.err; echo "big write rc $?"
   mkdir -p $Bg/out; python tools/refresh_pmc.py $Bg profiles/${tag}_65536_rocprofv3.md $Bg/out; cp $Bg/out/latest_pmc.json $O/pmc_65536.json; cp $Bg/out/${tag}_65536_rocprofv3.md $O/ 2>/dev/null
